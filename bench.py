@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark: shuffled GB/s (partition+exchange) for BASELINE.json's workload.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            (N=1 by default)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line: value, the
+milliseconds one timed step took (ms_per_step) and the configuration.  --dump-outputs DIR
+also writes what the last timed step computed (DIR/*.npy).  Everything else this file
+measures or checks runs only with --full (the paragraph at the end).
 
 A step is one pass of the hot path over one batch: every rank partitions its own batch of
 records resident in HBM (the single-pass padded write: sampled histogram, K4 stable
@@ -12,10 +17,10 @@ their IPC-mapped receive buffers over xGMI).  Weak scaling: 2^28 records per GPU
 at N=1; config C2's 2^31 total at N=8).  value = record bytes x records of all ranks /
 max-rank time.
 
-Also reported (rank 0): the roofline of the dominant kernel (K4 scatter) from HIP events
-on the engine's compute stream over the timed region, the stage breakdown, and the CPU
-baseline (the oracle's multi-threaded C restatement, timed on this host on a bounded
-sample of the same workload).
+With --full also reported (rank 0): the roofline of the dominant kernel (K4 scatter) from
+HIP events on the engine's compute stream, the stage breakdown, the lengths check, the
+fetch / Kryo read legs, the exchange's byte counts, and the CPU baseline (the oracle's
+multi-threaded C restatement, timed on this host on a bounded sample of the same workload).
 """
 from __future__ import annotations
 
@@ -39,6 +44,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the live PMC passes, "
+                         "the K4 and map-side rooflines, the stage breakdown, the lengths check, the exchange's "
+                         "byte counts and xGMI roofline, the fetch / Kryo read legs and the CPU baseline (the "
+                         "--no-* and --roofline-steps options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps write what the last one computed, as a caller reads it back, "
+                         "to DIR/*.npy (float64, every value exact): partition_lengths (sgx_map_lengths), "
+                         "sample_reducers (a fixed seeded choice) and sample_blocks (sgx_fetch_blocks of those "
+                         "reducers' blocks, back to back, as little-endian 32-bit words)")
     ap.add_argument("--workload", choices=["c1", "c3", "c4"], default="c1",
                     help="c1/c2: uniform 16 B records, R=1024 (the default line); c3: Zipf(1.1) keys, "
                          "R=4096; c4: TeraSort 100 B records (10 B keys), RangePartitioner R=1024 with "
@@ -107,6 +122,10 @@ def parse():
     a.placement = a.placement or ("bytes" if a.workload == "c3" else "even")
     if a.record_bytes != 16 and (a.serializer != "fixed" or a.dist != "uniform"):
         ap.error("c4 (100 B TeraSort records) runs with the fixed codec and its own key generator")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs writes one GPU's map output (N=1)")
     return a
 
 
@@ -281,6 +300,39 @@ def live_pmc(args):
             "source": "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over tools/prof_map.py in this bench run"}
 
 
+DUMP_BLOCK_BYTES = 24 << 20  # sampled block bytes per dump: 48 MiB as float64 words
+
+
+def dump_outputs(eng, sid, mid, R, seed, out_dir):
+    """--dump-outputs: what a caller of the timed path receives for map ``mid``, the one the
+    last timed step wrote, as float64 arrays (every value exact) under ``out_dir``:
+    partition_lengths [R], the map's byte length per reducer (sgx_map_lengths);
+    sample_reducers, reducers taken in the order of a seeded permutation of 0..R-1 while their
+    blocks fit in DUMP_BLOCK_BYTES together (a block that does not fit is passed over; if none
+    fits, the first reducer alone, its block cut at DUMP_BLOCK_BYTES); sample_blocks, those
+    blocks' bytes as sgx_fetch_blocks returns them, back to back, zero-padded to a multiple of
+    4 and read as little-endian 32-bit words."""
+    import numpy as np
+
+    lens = eng.map_lengths(sid, mid, R)
+    order = np.random.default_rng(seed).permutation(R)
+    pick, total = [], 0
+    for r in order:
+        if total + int(lens[r]) <= DUMP_BLOCK_BYTES:
+            pick.append(int(r))
+            total += int(lens[r])
+    if total == 0:
+        pick = [int(order[0])]
+    data, _ = eng.fetch_blocks(sid, [mid] * len(pick), pick)
+    data = data[:DUMP_BLOCK_BYTES]
+    words = np.zeros((len(data) + 3) // 4 * 4, dtype=np.uint8)
+    words[:len(data)] = data
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("partition_lengths", lens), ("sample_reducers", np.asarray(pick, dtype=np.int64)),
+                      ("sample_blocks", words.view("<u4"))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr.astype(np.float64))
+
+
 def _exchange_name(args, world, self_x):
     if world == 1 and not self_x:
         return None
@@ -316,7 +368,8 @@ def main():
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE {world}; using WORLD_SIZE", file=sys.stderr)
     # this run's HBM bytes first, in child processes, before this one touches the GPU
     live = None
-    if world == 1 and not args.no_live_pmc and args.serializer == "fixed" and not args.self_exchange:
+    if (args.full and world == 1 and not args.no_live_pmc and args.serializer == "fixed"
+            and not args.self_exchange):
         live = live_pmc(args)
     import numpy as np
     import torch
@@ -439,7 +492,8 @@ def main():
         for f in jobs:
             f.result()
 
-    run(max(args.warmup, tasks))
+    # exactly --warmup steps; concurrent map tasks need one each to open their streams
+    run(args.warmup if tasks == 1 else max(args.warmup, tasks))
     barrier()
     eng.stats_reset()
     barrier()
@@ -452,6 +506,31 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     st = eng.stats()
+    if args.dump_outputs:
+        dump_outputs(eng, sid, last["mid"], R, args.seed, args.dump_outputs)
+
+    def finish():
+        eng.unregister_shuffle(sid)
+        buf.free()
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # the plain run ends here: the headline figure and the configuration it was taken at
+        if rank == 0:
+            print(json.dumps({
+                "metric": METRIC, "value": round(float(rb) * n * world * args.steps / dt / 1e9, 2), "unit": "GB/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(dt * 1e3 / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "int64", "full": False,
+                "config": {"workload": _workload_name(args, n, R, world, self_x), "map_tasks": tasks,
+                           "batches": nbatch, "records_per_gpu": n, "partitions": R, "record_bytes": rb,
+                           "exchange": _exchange_name(args, world, self_x),
+                           "overlap_writes": not args.no_overlap_writes},
+            }), flush=True)
+        finish()
+        return
     # The K4 roofline from launches that do not overlap.  With overlapping writes
     # (the engine's default) a K4 is dispatched while the previous one's last workgroups still
     # run, so its HIP-event interval -- and its rocprofv3 duration -- include the wait for their
@@ -592,6 +671,7 @@ def main():
                 (2 * rb + rb / 128.0) if padded else 3 * rb),
             "verified_lengths_sum": verified,
         }
+        out["full"] = True
         if xgmi is not None:
             out["xgmi_roofline"] = xgmi
         if xbytes is not None:
@@ -662,11 +742,7 @@ def main():
         elif world == 1:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
-    eng.unregister_shuffle(sid)
-    buf.free()
-    eng.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

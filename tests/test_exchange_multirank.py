@@ -364,7 +364,7 @@ def test_bench_multi_rank_path_rehearsal(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
            "--gpus", "2", "--comm", "host", "--records", str(1 << 20), "--partitions", "64", "--steps", "3",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

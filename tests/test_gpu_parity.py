@@ -801,7 +801,7 @@ def test_memory_pool_size_classes_and_reuse(sgx_lib, oracle_lib):
 
 @pytest.mark.parametrize("workload", ["c3", "c4"])
 def test_bench_other_workloads_json_line(workload):
-    """bench.py --workload c3 | c4 at a small size: one JSON line with the contract's keys,
+    """bench.py --full --workload c3 | c4 at a small size: one JSON line with the contract's keys,
     the verified lengths, and the workload's record width and partition count."""
     import json
     import os
@@ -810,7 +810,7 @@ def test_bench_other_workloads_json_line(workload):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--records", str(1 << 20),
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -822,3 +822,43 @@ def test_bench_other_workloads_json_line(workload):
     assert d["config"]["record_bytes"] == (100 if workload == "c4" else 16)
     assert d["config"]["partitions"] == (4096 if workload == "c3" else 1024)
     assert d["roofline"]["algo_bytes_per_record"] == 2 * d["config"]["record_bytes"]
+
+
+def test_bench_plain_run_dumps_last_step_outputs(oracle_lib, tmp_path):
+    """A plain bench.py run (no --full) at a small size: --steps sets the steps, the result line
+    holds the headline keys and none of --full's legs, and --dump-outputs writes the last step's
+    map output as float64 arrays that equal the oracle's write of the same seeded input: the
+    partition lengths, and the sampled reducers' blocks word for word."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, R, seed = (1 << 20) + 3, 1024, 0x5EEDC0DE
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--records", str(n), "--steps", "3",
+           "--warmup", "1", "--dump-outputs", out]
+    p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    # value is the bytes of one step over ms_per_step (which is rounded to 0.1 us)
+    assert d["value"] == pytest.approx(16.0 * n / (d["ms_per_step"] * 1e-3) / 1e9, rel=0.01)
+    for k in ("cpu_baseline", "roofline", "roofline_map_side", "fetch_all_blocks", "verified_lengths_sum"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["partition_lengths.npy", "sample_blocks.npy", "sample_reducers.npy"]
+    lens, blocks, pick = (np.load(os.path.join(out, f + ".npy"))
+                          for f in ("partition_lengths", "sample_blocks", "sample_reducers"))
+    assert lens.dtype == blocks.dtype == pick.dtype == np.float64
+    assert lens.nbytes + blocks.nbytes + pick.nbytes <= 64_000_000
+    want_out, want_counts = oracle_lib.map_write(oracle_lib.gen_uniform16(n, seed), R)
+    assert np.array_equal(lens, want_counts * 16.0)
+    # every block fits the sample at this size, so the sample is the seeded permutation of all reducers
+    assert np.array_equal(pick, np.random.default_rng(seed).permutation(R))
+    off = oracle_lib.offsets(want_counts)
+    want = np.concatenate([want_out[off[r]:off[r + 1]].reshape(-1) for r in pick.astype(np.int64)])
+    assert np.array_equal(blocks, want.view("<u4").astype(np.float64))

@@ -12,9 +12,9 @@ if [ "$2" != "skip-tests" ]; then
   timeout -k 10 900 python -u -m pytest tests -m "gpu and not slow" -x -q --timeout 300 --timeout-method thread \
     > "$out/pytest_gpu.log" 2>&1
 fi
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > "$out/bench.log" 2>&1
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 > "$out/bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/prof" -o run -- \
-  python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > "$out/prof.log" 2>&1
+  python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > "$out/prof.log" 2>&1
 timeout -k 10 300 python3 -u tools/multimap_probe.py > "$out/multimap.log" 2>&1
 timeout -k 10 600 python3 -u tools/sweep_scatter.py --rounds 3 --iters 3 \
   --variants 0:0:0,256:12:10,256:16:7,256:8:8,256:4:16,512:4:16 > "$out/sweep.log" 2>&1

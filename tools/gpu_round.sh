@@ -12,11 +12,11 @@ if [ "$2" != "skip-tests" ]; then
     > "$out/pytest_gpu.log" 2>&1
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1
 fi
-timeout -k 10 300 python -u bench.py > "$out/bench.log" 2>&1
+timeout -k 10 300 python -u bench.py --full > "$out/bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -o run -- \
-  python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > "$out/kt.log" 2>&1
+  python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$out/kt.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -o run -- \
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$out/fetch.log" 2>&1
+  python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > "$out/fetch.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write" -o run -- \
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$out/write.log" 2>&1
+  python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > "$out/write.log" 2>&1
 echo done > "$out/DONE"
