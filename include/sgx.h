@@ -211,7 +211,12 @@ int sgx_lz4_unframe_streams(sgx_engine *e, const void *framed_dev, const int64_t
  * key} per distinct key, partitioned by the shuffle's partitioner, keys ascending within a
  * partition (Spark's PartitionedAppendOnlyMap iteration order is unspecified; this is the
  * canonical order the parity tests compare).  Set before the first write (SGX_ERR_STATE
- * after).  sgx_read_grouped(SGX_AGG_SUM) on such a shuffle is combineCombinersByKey. */
+ * after).  sgx_read_grouped(SGX_AGG_SUM) on such a shuffle is combineCombinersByKey.
+ * SGX_AGG_MIN / SGX_AGG_MAX / SGX_AGG_COUNT likewise: the combiner is the signed minimum /
+ * maximum of the map's values of the key, or the number of the map's records with the key
+ * (createCombiner = 1, mergeValue = c + 1); the reader merges with min / max / sum of counts
+ * (sgx_read_grouped with the same aggregation; any other is SGX_ERR_UNSUPPORTED).
+ * SGX_AGG_GROUP (groupByKey never combines map-side) and unknown values: SGX_ERR_UNSUPPORTED. */
 int sgx_set_map_side_combine(sgx_engine *e, int32_t shuffle_id, int32_t agg);
 /* The map writer Spark runs for the shuffle's handle.  SortShuffleManager.registerShuffle
  * (inherited, shuffle/ucx/CommonUcxShuffleManager.scala:25) gives a dependency with a
@@ -443,10 +448,19 @@ int sgx_read_records(sgx_engine *e, int32_t shuffle_id, const int64_t *map_ids, 
  *                               values[N] (every value, grouped).
  *   SGX_AGG_SUM   (reduceByKey(_ + _)): keys[G], values[G] = wrapping Long sums;
  *                               group_starts may be NULL.
+ *   SGX_AGG_MIN / SGX_AGG_MAX (reduceByKey(math.min) / reduceByKey(math.max)): keys[G],
+ *                               values[G] = the signed-Long minimum / maximum of the group's
+ *                               values; group_starts may be NULL.
+ *   SGX_AGG_COUNT (combineByKey(_ => 1L, (c, _) => c + 1, _ + _)): keys[G], values[G] = the
+ *                               group's record count; group_starts may be NULL.
+ * For every reducing aggregation *out_values == *out_groups.  On a map-side-combined shuffle
+ * (sgx_set_map_side_combine) the read is combineCombinersByKey (:158-161) and takes only the
+ * shuffle's own aggregation (SGX_ERR_UNSUPPORTED otherwise): MIN / MAX merge with min / max,
+ * COUNT merges the maps' counts by wrapping sum (Aggregator.mergeCombiners, not mergeValue).
  * Capacities in elements: cap_groups for keys / group_starts, cap_values for values.  A call
  * with keys NULL and both capacities 0 only reports *out_groups / *out_values.  Output memory
  * kind: mem_kind (all three arrays). */
-enum sgx_agg { SGX_AGG_GROUP = 0, SGX_AGG_SUM = 1 };
+enum sgx_agg { SGX_AGG_GROUP = 0, SGX_AGG_SUM = 1, SGX_AGG_MIN = 2, SGX_AGG_MAX = 3, SGX_AGG_COUNT = 4 };
 int sgx_read_grouped(sgx_engine *e, int32_t shuffle_id, const int64_t *map_ids, int64_t nmaps,
                      int32_t start_partition, int32_t end_partition, int32_t agg, int64_t *keys,
                      int64_t *group_starts, int64_t *values, int64_t cap_groups, int64_t cap_values,

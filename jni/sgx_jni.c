@@ -469,9 +469,10 @@ JNIEXPORT jlong JNICALL JNI_FN(readSorted)(JNIEnv *env, jclass c, jlong e, jint 
     return check(env, rc) ? -1 : bytes;
 }
 
-/* readGrouped: {groups, values, records}; agg 0 = groupByKey (keys, groupStarts, values), 1 = sum
- * (keys, sums in values); records = the shuffled records the aggregation consumed (the reader's
- * incRecordsRead).  Null buffers with their capacities 0 = size query. */
+/* readGrouped: {groups, values, records}; agg 0 = groupByKey (keys, groupStarts, values), every
+ * reducing agg -- 1 = sum, 2 = min, 3 = max, 4 = count -- (keys, one reduced value per key in
+ * values; groupStarts may be null); records = the shuffled records the aggregation consumed (the
+ * reader's incRecordsRead).  Null buffers with their capacities 0 = size query. */
 JNIEXPORT jlongArray JNICALL JNI_FN(readGrouped)(JNIEnv *env, jclass c, jlong e, jint sid, jlongArray maps,
                                                  jint start, jint end, jint agg, jobject keys, jobject starts,
                                                  jobject values) {

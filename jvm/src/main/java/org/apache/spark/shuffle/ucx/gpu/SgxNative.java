@@ -26,7 +26,7 @@ public final class SgxNative {
   public static final int PART_HASH = 0, PART_RANGE_I64 = 1, PART_RANGE_BYTES10 = 2;
   public static final int SER_FIXED = 0, SER_KRYO = 1;
   public static final int CODEC_NONE = 0, CODEC_LZ4 = 1;
-  public static final int AGG_GROUP = 0, AGG_SUM = 1;
+  public static final int AGG_GROUP = 0, AGG_SUM = 1, AGG_MIN = 2, AGG_MAX = 3, AGG_COUNT = 4;
   public static final int PLACE_EVEN = 0, PLACE_BYTES = 1;  // sgx_placement
   public static final int WRITER_SORT = 0, WRITER_UNSAFE = 1;  // sgx_map_writer
 

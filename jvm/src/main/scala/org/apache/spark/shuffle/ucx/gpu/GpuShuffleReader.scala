@@ -9,6 +9,10 @@
  *    fetch runs on the GPU over HBM-resident blocks:
  *      declared "sum" aggregator (reduceByKey(_ + _): combineValuesByKey, or
  *        combineCombinersByKey after a map-side combine, :155-164)  -> readGrouped(AGG_SUM)
+ *      declared "min" / "max" aggregator (reduceByKey(math.min / math.max),
+ *        with or without map-side combine)                   -> readGrouped(AGG_MIN / AGG_MAX)
+ *      declared "count" aggregator (combineByKey(_ => 1L, (c, _) => c + 1, _ + _);
+ *        map-side counts are merged by sum)                         -> readGrouped(AGG_COUNT)
  *      declared "group" aggregator (groupByKey)                      -> readGrouped(AGG_GROUP)
  *      keyOrdering (sortByKey, :166-181)                             -> readSorted
  *      neither (deserializeStream, :137-145)                         -> readRecords
@@ -140,7 +144,7 @@ class GpuShuffleReader[K, C](engine: Long, handle: GpuShuffleHandle[K, _, C], st
 
   private def readOnGpu(maps: Array[Long], a: Int, b: Int): Iterator[Product2[K, C]] = {
     if (handle.agg != GpuUcxShuffleManager.NO_AGG) {
-      val sum = handle.agg == SgxNative.AGG_SUM
+      val reducing = handle.agg != SgxNative.AGG_GROUP  // sum / min / max / count: one Long per key
       val Array(groups, values, _) = SgxNative.readGrouped(engine, shuffleId, maps, a, b, handle.agg, null, null, null)
       val keys = le(groups * 8); val starts = le(groups * 8); val vals = le(values * 8)
       val Array(_, _, consumed) = SgxNative.readGrouped(engine, shuffleId, maps, a, b, handle.agg, keys, starts, vals)
@@ -148,7 +152,7 @@ class GpuShuffleReader[K, C](engine: Long, handle: GpuShuffleHandle[K, _, C], st
       // (spark_3_0/UcxShuffleReader.scala:148-162)
       readMetrics.incRecordsRead(consumed)
       val k = keys.asLongBuffer(); val s = starts.asLongBuffer(); val v = vals.asLongBuffer()
-      if (sum) {
+      if (reducing) {
         Iterator.tabulate(groups.toInt)(g => (k.get(g), v.get(g)).asInstanceOf[Product2[K, C]])
       } else {
         // groupByKey's combiner type is CompactBuffer[V], values in arrival order

@@ -9,10 +9,13 @@
  *     writer);
  *   - a HashPartitioner, or a RangePartitioner over Long keys;
  *   - no aggregator, or one DECLARED with spark.shuffle.ucx.gpu.aggregator.<shuffleId> =
- *     "sum" (reduceByKey(_ + _) on Longs: the GPU sums with wrap-around, map-side combine
- *     allowed) or "group" (groupByKey: mapSideCombine must be false).  Spark cannot look
- *     inside an aggregator's closures, so an undeclared one -- reduceByKey(math.max),
- *     combineByKey(...) -- stays on the CPU path instead of being guessed.
+ *     "sum" (reduceByKey(_ + _) on Longs: the GPU sums with wrap-around), "min" / "max"
+ *     (reduceByKey(math.min) / reduceByKey(math.max): signed Long compare), "count"
+ *     (combineByKey(_ => 1L, (c, _) => c + 1, _ + _): the combiner is a Long record count,
+ *     merged by sum) -- map-side combine allowed for these four -- or "group" (groupByKey:
+ *     mapSideCombine must be false).  Spark cannot look inside an aggregator's closures, so
+ *     an undeclared one -- reduceByKey(_ * _), aggregateByKey(...) -- stays on the CPU path
+ *     instead of being guessed.
  * Everything else falls back to SortShuffleManager's own writer and reader.
  *
  *   - a compressed Kryo shuffle only with spark.io.compression.codec = lz4 (the GPU frames
@@ -40,7 +43,7 @@ import org.apache.spark.shuffle.sort.{SortShuffleManager, SortShuffleWriter}
  *  every GpuRunExchange, so an executor that never ran a task of the shuffle registers it
  *  before joining the shuffle's collective (instead of failing it). */
 case class GpuShuffleSpec(shuffleId: Int, numPartitions: Int, kind: Int, bounds: Array[Long], ascending: Boolean,
-                          kryo: Boolean, lz4Block: Int, combineSum: Boolean, writerUnsafe: Boolean,
+                          kryo: Boolean, lz4Block: Int, combine: Int, writerUnsafe: Boolean,
                           placementBytes: Boolean)
 
 /** A shuffle the GPU runs: same fields as BaseShuffleHandle, plus the declared aggregation and
@@ -84,6 +87,9 @@ class GpuUcxShuffleManager(conf: SparkConf, isDriver: Boolean) extends SortShuff
     if (dep.aggregator.isEmpty) Some(NO_AGG)
     else conf.get("spark.shuffle.ucx.gpu.aggregator." + shuffleId, "") match {
       case "sum" => Some(SgxNative.AGG_SUM)
+      case "min" => Some(SgxNative.AGG_MIN)
+      case "max" => Some(SgxNative.AGG_MAX)
+      case "count" => Some(SgxNative.AGG_COUNT)
       case "group" if !dep.mapSideCombine => Some(SgxNative.AGG_GROUP)
       case _ => None
     }
@@ -127,7 +133,8 @@ class GpuUcxShuffleManager(conf: SparkConf, isDriver: Boolean) extends SortShuff
       if (kryo && conf.getBoolean("spark.shuffle.compress", true))
         conf.getSizeAsBytes("spark.io.compression.lz4.blockSize", "32k").toInt
       else 0,
-      dep.mapSideCombine && agg == SgxNative.AGG_SUM,
+      // the operator the map side combines with (every reducing aggregator), NO_AGG for none
+      if (dep.mapSideCombine && agg != NO_AGG && agg != SgxNative.AGG_GROUP) agg else NO_AGG,
       // the writer Spark's own handle would run (SortShuffleManager.registerShuffle; the
       // reference's getWriter, spark_3_0/UcxShuffleManager.scala:32-53): UnsafeShuffleWriter for
       // a SerializedShuffleHandle, whose fast spill merge keeps each spill's partition segment
@@ -157,7 +164,7 @@ class GpuUcxShuffleManager(conf: SparkConf, isDriver: Boolean) extends SortShuff
         SgxNative.setSerializer(engine, sp.shuffleId, SgxNative.SER_KRYO)
         if (sp.lz4Block > 0) SgxNative.setCompression(engine, sp.shuffleId, SgxNative.CODEC_LZ4, sp.lz4Block)
       }
-      if (sp.combineSum) SgxNative.setMapSideCombine(engine, sp.shuffleId, SgxNative.AGG_SUM)
+      if (sp.combine != NO_AGG) SgxNative.setMapSideCombine(engine, sp.shuffleId, sp.combine)
       if (sp.writerUnsafe) SgxNative.setMapWriter(engine, sp.shuffleId, SgxNative.WRITER_UNSAFE)
       if (sp.placementBytes) SgxNative.setReducerPlacement(engine, sp.shuffleId, SgxNative.PLACE_BYTES)
       registered.put(sp.shuffleId, true)

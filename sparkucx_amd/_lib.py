@@ -20,7 +20,7 @@ SGX_ERR_INVALID, SGX_ERR_STATE, SGX_ERR_HIP, SGX_ERR_COMM = -1, -2, -3, -4
 SGX_ERR_IO, SGX_ERR_NOMEM, SGX_ERR_NOT_FOUND, SGX_ERR_UNSUPPORTED, SGX_ERR_TIMEOUT = -5, -6, -7, -8, -9
 PART_HASH, PART_RANGE_I64, PART_RANGE_BYTES10 = 0, 1, 2
 MEM_HOST, MEM_DEVICE, MEM_DEVICE_RETAINED = 0, 1, 2
-AGG_GROUP, AGG_SUM = 0, 1
+AGG_GROUP, AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT = 0, 1, 2, 3, 4
 SER_FIXED, SER_KRYO = 0, 1
 STAGES = ("hist", "scan", "scatter", "allgather", "alltoall", "regroup", "sort", "group", "serialize",
           "deserialize", "combine", "compress", "decompress")

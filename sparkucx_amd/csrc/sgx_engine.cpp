@@ -421,12 +421,14 @@ extern "C" int sgx_set_map_side_combine(sgx_engine *e, int32_t shuffle_id, int32
     if (!e) return fail_msg(SGX_ERR_INVALID, "engine is NULL");
     std::shared_ptr<Shuffle> s = e->find_shuffle(shuffle_id);
     if (!s) return SGX_ERR_STATE;
-    if (agg != SGX_AGG_SUM && agg != -1)
-        return fail_msg(SGX_ERR_UNSUPPORTED, "map-side combine supports SGX_AGG_SUM (reduceByKey), not %d", agg);
+    const bool reducing = agg == SGX_AGG_SUM || agg == SGX_AGG_MIN || agg == SGX_AGG_MAX || agg == SGX_AGG_COUNT;
+    if (!reducing && agg != -1)
+        return fail_msg(SGX_ERR_UNSUPPORTED,
+                        "map-side combine supports SGX_AGG_SUM / _MIN / _MAX / _COUNT (reduceByKey), not %d", agg);
     if (!s->configurable()) return fail_msg(SGX_ERR_STATE, "shuffle %d already has map outputs", shuffle_id);
-    if (agg == SGX_AGG_SUM && (s->rb != 16 || s->kind == SGX_PART_RANGE_BYTES10))
+    if (reducing && (s->rb != 16 || s->kind == SGX_PART_RANGE_BYTES10))
         return fail_msg(SGX_ERR_UNSUPPORTED, "map-side combine needs (Long, Long) 16 B records");
-    if (agg == SGX_AGG_SUM && s->writer == SGX_WRITER_UNSAFE)
+    if (reducing && s->writer == SGX_WRITER_UNSAFE)
         return fail_msg(SGX_ERR_STATE, "shuffle %d runs UnsafeShuffleWriter, which never combines", shuffle_id);
     s->combine = agg;
     return SGX_OK;

@@ -490,10 +490,12 @@ int fetch_impl(sgx_engine *e, Ctx &c, Shuffle &s, const int64_t *map_ids, const 
                void *dst, int64_t dst_cap, int32_t dst_mem_kind, int64_t *out_lengths, bool sync,
                std::vector<std::shared_ptr<void>> *keep);
 // Group n key-sorted (Long, Long) records (device) by key, synchronously: *ngroups, and
-// device arrays in the context's grp_out: keys[G], starts[G] (may be NULL), vals[G] sums
-// (SGX_AGG_SUM) or vals[n] every value (SGX_AGG_GROUP).
-int group_records(sgx_engine *e, Ctx &c, const void *sorted, int64_t n, int32_t agg, int64_t *ngroups,
-                  int64_t **keys, int64_t **starts, int64_t **vals);
+// device arrays in the context's grp_out: keys[G], starts[G] (may be NULL), vals[G] the
+// groups' sum / min / max / count (SGX_AGG_SUM / _MIN / _MAX / _COUNT) or vals[n] every value
+// (SGX_AGG_GROUP).  combine: the map-side combine the records went through (Shuffle::combine;
+// -1 = raw records, mergeValue).  Combiners merge with mergeCombiners: COUNT's are summed.
+int group_records(sgx_engine *e, Ctx &c, const void *sorted, int64_t n, int32_t agg, int32_t combine,
+                  int64_t *ngroups, int64_t **keys, int64_t **starts, int64_t **vals);
 // Stable sort of n 16 B / 100 B records in c.sort_buf[0] by key, then by the shuffle's
 // partitioner (when `by_partition`): *sorted = the buffer holding the result.
 // nparts: partitions present in the records (a read's reducer range; 0 = all R), which sizes

@@ -305,11 +305,15 @@ hipError_t launch_piece_hist(const void *in, int64_t n, const int64_t *desc, int
                              uint32_t *cnt, hipStream_t st);
 hipError_t launch_seg_offsets(const uint32_t *cnt, const int64_t *seg_base, const int32_t *pk, int64_t nseg, uint32_t Q,
                               uint32_t *offs, hipStream_t st);
-// groupByKey / reduceByKey(_ + _) over key-sorted (Long, Long) records in one pass
-// (sgx_reduce.hip, k_group_fused): keys[g], starts[g] (may be NULL), vals = every value (GROUP)
-// or the group sums (SUM), *ngroups.  status: 2 * group_tiles(n) u64, ticket/err: zeroed.
+// groupByKey / reduceByKey over key-sorted (Long, Long) records in one pass (sgx_reduce.hip,
+// k_group_fused): keys[g], starts[g] (may be NULL), vals = every value (GROUP_OP_NONE) or one
+// value per group (the operator's reduction), *ngroups.  status: 2 * group_tiles(n) u64,
+// ticket/err: zeroed.
+// The operator of the segmented scan: none (groupByKey), wrapping sum, signed min / max, or a
+// count of the group's records (the values are not read).
+enum GroupOp { GROUP_OP_NONE = 0, GROUP_OP_SUM = 1, GROUP_OP_MIN = 2, GROUP_OP_MAX = 3, GROUP_OP_COUNT = 4 };
 int64_t group_tiles(int64_t n);
-hipError_t launch_group_fused(const void *rec, int64_t n, bool sum, uint64_t *status, uint32_t *ticket, uint32_t *err,
+hipError_t launch_group_fused(const void *rec, int64_t n, int op, uint64_t *status, uint32_t *ticket, uint32_t *err,
                               int64_t *keys, int64_t *starts, int64_t *vals, int64_t *ngroups, hipStream_t st);
 // keys[i], vals[i] -> 16 B records {key, value} (map-side combine output)
 hipError_t launch_pack_pairs(const int64_t *keys, const int64_t *vals, int64_t n, void *out, hipStream_t st);

@@ -698,14 +698,16 @@ static int serialize_kryo(sgx_engine *e, Ctx &c, Shuffle &s, MapOut &m, const ui
     return SGX_OK;
 }
 
-// Map-side combine, SGX_AGG_SUM (ExternalSorter.insertAll with the aggregator's
-// mergeValue; the canonical combiner order is (partition, key ascending)): the n records at
+// Map-side combine, SGX_AGG_SUM / _MIN / _MAX / _COUNT (ExternalSorter.insertAll with the
+// aggregator's createCombiner / mergeValue; the canonical combiner order is (partition, key
+// ascending)): the n records at
 // `in` (device) are copied to the context's sort buffer, sorted stably by key and then by
 // the shuffle's partitioner (LSD digit passes + one partition pass, sgx_read.cpp), grouped,
-// summed (wrapping), packed back into {key, sum} records and partitioned into m.data (an
+// reduced (s.combine's operator on the raw values: a wrapping sum, a signed min / max, or
+// the records counted), packed back into {key, combiner} records and partitioned into m.data (an
 // identity permutation that yields the partition offsets through the usual machinery).
 // Synchronous (the group count decides the output size).
-static int combine_sum(sgx_engine *e, Ctx &c, Shuffle &s, MapOut &m, const void *in, int64_t n) {
+static int combine_map(sgx_engine *e, Ctx &c, Shuffle &s, MapOut &m, const void *in, int64_t n) {
     hipStream_t st = c.st;
     hipEvent_t t0 = e->ev(), t1 = e->ev();
     HIP_TRY(hipEventRecord(t0, st));
@@ -714,13 +716,13 @@ static int combine_sum(sgx_engine *e, Ctx &c, Shuffle &s, MapOut &m, const void 
     if (n > 0) HIP_TRY(hipMemcpyAsync(c.sort_buf[0].p, in, (size_t)n * 16, hipMemcpyDeviceToDevice, st));
     const void *sorted = c.sort_buf[0].p;
     int64_t ng = 0;
-    int64_t *keys = nullptr, *sums = nullptr;
+    int64_t *keys = nullptr, *combs = nullptr;
     if (n > 0) {
         SGX_TRY(sort_records(e, c, s, n, true, &sorted));
-        SGX_TRY(group_records(e, c, sorted, n, SGX_AGG_SUM, &ng, &keys, nullptr, &sums));
+        SGX_TRY(group_records(e, c, sorted, n, s.combine, -1, &ng, &keys, nullptr, &combs));
     }
     SGX_TRY(c.comb_buf.ensure((size_t)std::max<int64_t>(ng, 1) * 16));
-    HIP_TRY(launch_pack_pairs(keys, sums, ng, c.comb_buf.p, st));
+    HIP_TRY(launch_pack_pairs(keys, combs, ng, c.comb_buf.p, st));
     m.nrec = ng;
     SGX_TRY(m.data.ensure((size_t)std::max<int64_t>(ng, 1) * 16));
     SGX_TRY(partition_pass(e, c, c.comb_buf.p, m.data.p, ng, 16, s.pp, s.R, s.kind, (uint32_t *)m.part_off.p,
@@ -748,8 +750,8 @@ static int run_map_pipeline(sgx_engine *e, Ctx &c, Shuffle &s, MapOut &m, const 
     int tail = -1;  // the padded write left its tail on c.st_tail (this slot's pad_done)
     PadGeom pg;
     if (!partitioned && !no_pad && use_padded(e, s, in, n)) pg = pad_geom(e, s, n, ct);
-    if (s.combine == SGX_AGG_SUM) {
-        SGX_TRY(combine_sum(e, c, s, m, partitioned ? m.data.p : in, n));
+    if (s.combine != -1) {
+        SGX_TRY(combine_map(e, c, s, m, partitioned ? m.data.p : in, n));
         rec_off_dev = c.last_off_dev;
     } else if (!partitioned && pg.olim >= n) {
         m.nrec = n;

@@ -555,10 +555,26 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
     return SGX_OK;
 }
 
-int sgx::group_records(sgx_engine *e, Ctx &c, const void *sorted, int64_t n, int32_t agg, int64_t *ngroups,
-                       int64_t **keys, int64_t **starts, int64_t **vals) {
+// The scan's operator for aggregation `agg` over records that went through map-side combine
+// `combine` (-1: raw records).  Aggregator.mergeValue on raw records, mergeCombiners on
+// combiners: they differ for COUNT, whose combiners (the maps' counts) are summed.
+static int group_op(int32_t agg, int32_t combine) {
+    switch (agg) {
+    case SGX_AGG_GROUP: return GROUP_OP_NONE;
+    case SGX_AGG_SUM: return GROUP_OP_SUM;
+    case SGX_AGG_MIN: return GROUP_OP_MIN;
+    case SGX_AGG_MAX: return GROUP_OP_MAX;
+    case SGX_AGG_COUNT: return combine == SGX_AGG_COUNT ? GROUP_OP_SUM : GROUP_OP_COUNT;
+    }
+    return -1;
+}
+
+int sgx::group_records(sgx_engine *e, Ctx &c, const void *sorted, int64_t n, int32_t agg, int32_t combine,
+                       int64_t *ngroups, int64_t **keys, int64_t **starts, int64_t **vals) {
     hipStream_t st = c.st;
     *ngroups = 0;
+    const int op = group_op(agg, combine);
+    if (op < 0) return fail_msg(SGX_ERR_INVALID, "unknown aggregation %d", agg);
     // one pass (k_group_fused): outputs sized for the worst case (every record its own group)
     if (n >= (int64_t)1 << 31) return fail_msg(SGX_ERR_UNSUPPORTED, "grouping %lld records (limit 2^31 - 1)", (long long)n);
     const int64_t tiles = group_tiles(n);
@@ -574,7 +590,7 @@ int sgx::group_records(sgx_engine *e, Ctx &c, const void *sorted, int64_t n, int
     int64_t ng = 0;
     if (n > 0) {
         HIP_TRY(hipMemsetAsync(c.grp_status.p, 0, (size_t)(16 + tiles * 16), st));
-        HIP_TRY(launch_group_fused(sorted, n, agg == SGX_AGG_SUM, (uint64_t *)((char *)c.grp_status.p + 16), ticket_err,
+        HIP_TRY(launch_group_fused(sorted, n, op, (uint64_t *)((char *)c.grp_status.p + 16), ticket_err,
                                    ticket_err + 1, dkeys, starts ? dstarts : nullptr, dvals, dng, st));
         uint32_t terr[2] = {0, 0};
         HIP_TRY(hipMemcpyAsync(&ng, dng, 8, hipMemcpyDeviceToHost, st));
@@ -742,16 +758,17 @@ extern "C" int sgx_read_grouped(sgx_engine *e, int32_t shuffle_id, const int64_t
                                 int32_t mem_kind, int64_t *out_groups, int64_t *out_values) {
     sgx::TraceRange trace_("sgx_read_grouped");
     if (!e || !out_groups || !out_values) return fail_msg(SGX_ERR_INVALID, "NULL argument");
-    if (agg != SGX_AGG_GROUP && agg != SGX_AGG_SUM) return fail_msg(SGX_ERR_INVALID, "unknown aggregation %d", agg);
+    if (agg < SGX_AGG_GROUP || agg > SGX_AGG_COUNT) return fail_msg(SGX_ERR_INVALID, "unknown aggregation %d", agg);
     std::shared_ptr<Shuffle> s;
     Ctx *c = nullptr;
     SGX_TRY(read_entry(e, shuffle_id, mem_kind, &s, &c));
     if (s->rb != 16)
         return fail_msg(SGX_ERR_UNSUPPORTED, "grouped read needs 16 B (Long, Long) records, not %d B", s->rb);
-    // a map-side-combined shuffle holds combiners: only combineCombinersByKey (sum) applies
-    if (s->combine == SGX_AGG_SUM && agg != SGX_AGG_SUM)
-        return fail_msg(SGX_ERR_UNSUPPORTED, "shuffle %d was combined map-side (sum): read it with SGX_AGG_SUM",
-                        shuffle_id);
+    // a map-side-combined shuffle holds combiners: only combineCombinersByKey of the same
+    // aggregator applies
+    if (s->combine != -1 && agg != s->combine)
+        return fail_msg(SGX_ERR_UNSUPPORTED, "shuffle %d was combined map-side (aggregation %d): read it with that, not %d",
+                        shuffle_id, s->combine, agg);
     const uint64_t epoch = e->epoch.load();
     int64_t n = 0, ng = 0;
     int64_t *dkeys = nullptr, *dstarts = nullptr, *dvals = nullptr;
@@ -765,7 +782,7 @@ extern "C" int sgx_read_grouped(sgx_engine *e, int32_t shuffle_id, const int64_t
         SGX_TRY(records_impl(e, *c, *s, map_ids, nmaps, start_partition, end_partition, &n));
         const void *sorted = nullptr;
         SGX_TRY(sort_records(e, *c, *s, n, true, &sorted, end_partition - start_partition));
-        SGX_TRY(group_records(e, *c, sorted, n, agg, &ng, &dkeys, &dstarts, &dvals));
+        SGX_TRY(group_records(e, *c, sorted, n, agg, s->combine, &ng, &dkeys, &dstarts, &dvals));
     }
     const int64_t nvals = agg == SGX_AGG_GROUP ? n : ng;
     c->last_read_records = n;  // the shuffled records the aggregation consumed

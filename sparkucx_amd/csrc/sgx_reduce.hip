@@ -7,6 +7,9 @@
 //     order: the canonical sequence of SURVEY §8(a)); the stable sort keeps it.
 //   * reduceByKey(_ + _) -- combineValuesByKey with a Long sum: wrapping 64-bit adds, so
 //     the order of additions does not change the result.
+//   * reduceByKey(min) / reduceByKey(max) / per-key counts -- the same combineValuesByKey
+//     with a signed-Long minimum, maximum, or a record count (createCombiner = 1,
+//     mergeValue = c + 1); a combined shuffle's counts merge by sum (mergeCombiners).
 //
 // Groups never span reducers: a key has one partition.  Layout: records {i64 key, i64
 // value} little-endian, 16 B each, n < 2^31.
@@ -22,14 +25,19 @@ constexpr int RT = 256;  // threads per workgroup
 
 // groupByKey / reduceByKey(_ + _) over the key-sorted records in ONE pass (k_group_fused):
 // a tile of GTILE records is read once, coalesced; each thread walks a contiguous run of GI of
-// them (keys -- and values for SUM -- staged in LDS), flags key changes, and the tile's
+// them (keys -- and values for SUM / MIN / MAX -- staged in LDS), flags key changes, and the tile's
 // offset comes from a decoupled look-back over the tiles in ticket order.  The scanned value
 // is a segmented sum: (groups started, sum of the group still open at the end, any start),
 // combined left to right as (c1 + c2, f2 ? s2 : s1 + s2, f1 | f2), so a group's Long sum is
-// complete when the next group starts, wherever its records lie.
+// complete when the next group starts, wherever its records lie.  The operator is a template
+// parameter: `+` stands for the operator's combine and "nothing yet" for its identity
+// (gop_id: 0, INT64_MAX for MIN, INT64_MIN for MAX) -- in the thread's start value, the
+// restart at a group start, the wave / tile prefixes and the look-back's padding lanes alike.
 //   keys[g], starts[g] = key and first record of group g (starts may be NULL);
 //   GROUP: vals[i] = value of record i (groups are contiguous runs, arrival order kept);
 //   SUM:   vals[g] = wrapping 64-bit sum of group g's values;
+//   MIN / MAX: vals[g] = signed minimum / maximum of group g's values;
+//   COUNT: vals[g] = records of group g (a sum of ones: no value is staged);
 //   *ngroups = number of groups (written by the thread holding the last record).
 // Replaces four passes (flags, a scan, emit, and for SUM three prefix-sum kernels plus a
 // gather): one read of the records and the outputs' writes.
@@ -57,8 +65,20 @@ struct Seg {
     uint64_t c, s;
     uint32_t f;
 };
+// the scan's operator on Seg::s (64 raw bits; MIN / MAX compare them as signed Longs)
+template <int OP>
+__device__ __forceinline__ constexpr uint64_t gop_id() {
+    return OP == GROUP_OP_MIN ? (uint64_t)INT64_MAX : OP == GROUP_OP_MAX ? (uint64_t)INT64_MIN : 0ull;
+}
+template <int OP>
+__device__ __forceinline__ uint64_t gop(uint64_t a, uint64_t b) {
+    if constexpr (OP == GROUP_OP_MIN) return (int64_t)b < (int64_t)a ? b : a;
+    else if constexpr (OP == GROUP_OP_MAX) return (int64_t)b > (int64_t)a ? b : a;
+    else return a + b;
+}
+template <int OP>
 __device__ __forceinline__ Seg seg_combine(const Seg &l, const Seg &r) {
-    return Seg{l.c + r.c, r.f ? r.s : l.s + r.s, l.f | r.f};
+    return Seg{l.c + r.c, r.f ? r.s : gop<OP>(l.s, r.s), l.f | r.f};
 }
 __device__ __forceinline__ Seg seg_shfl_up(const Seg &x, int d) {
     return Seg{__shfl_up(x.c, d, 64), __shfl_up(x.s, d, 64), (uint32_t)__shfl_up((int)x.f, d, 64)};
@@ -80,14 +100,17 @@ __device__ __forceinline__ Seg gs_value(uint64_t w1, uint64_t w2) {
 }
 
 
-template <bool SUM>
+template <int OP>
 __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict__ rec, int64_t n,
                                                     uint64_t *st1, uint64_t *st2,
                                                     uint32_t *ticket, uint32_t *err, int64_t *__restrict__ keys,
                                                     int64_t *__restrict__ starts, int64_t *__restrict__ vals,
                                                     int64_t *__restrict__ ngroups) {
+    constexpr uint64_t ID = gop_id<OP>();                         // "nothing yet" in Seg::s
+    constexpr bool RED = OP != GROUP_OP_NONE;                     // one value per group (else every value)
+    constexpr bool VAL = RED && OP != GROUP_OP_COUNT;             // the values take part (staged in LDS)
     __shared__ uint64_t s_key[GTILE + GTILE / GI];                // then the tile's group keys
-    __shared__ uint64_t s_val[SUM ? GTILE + GTILE / GI : 1];      // then the tile's closed group sums
+    __shared__ uint64_t s_val[VAL ? GTILE + GTILE / GI : RED ? GTILE : 1];  // then the tile's closed group sums
     __shared__ uint16_t s_st[GTILE];                              // the tile's group starts (tile offsets)
     __shared__ uint64_t s_wc[GT / 64], s_ws[GT / 64];
     __shared__ uint32_t s_wf[GT / 64];
@@ -104,8 +127,8 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
         if (i < n) {
             const ulonglong2 r = rec[i];
             s_key[gslot(k * GT + tid)] = r.x;
-            if constexpr (SUM) s_val[gslot(k * GT + tid)] = r.y;
-            else gst(vals + i, (int64_t)r.y);
+            if constexpr (VAL) s_val[gslot(k * GT + tid)] = r.y;
+            else if constexpr (!RED) gst(vals + i, (int64_t)r.y);
         }
     }
     if (tid == 0) s_prev = t0 > 0 ? rec[t0 - 1].x : 0ull;
@@ -114,23 +137,24 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
     const int64_t i0 = t0 + (int64_t)tid * GI;
     uint64_t prev = tid == 0 ? s_prev : s_key[gslot(tid * GI - 1)];
     uint32_t fm = 0;
-    Seg a{0, 0, 0};
-    uint64_t kreg[GI], vreg[SUM ? GI : 1];
+    Seg a{0, ID, 0};
+    uint64_t kreg[GI], vreg[VAL ? GI : 1];
 #pragma unroll
     for (int k = 0; k < GI; ++k) {
         const int64_t i = i0 + k;
         kreg[k] = s_key[gslot(tid * GI + k)];
-        if constexpr (SUM) vreg[k] = s_val[gslot(tid * GI + k)];
+        if constexpr (VAL) vreg[k] = s_val[gslot(tid * GI + k)];
         if (i < n) {
             const uint64_t key = kreg[k];
             if (i == 0 || key != prev) {
                 fm |= 1u << k;
                 a.c += 1;
-                a.s = 0;
+                a.s = ID;
                 a.f = 1;
             }
             prev = key;
-            if constexpr (SUM) a.s += vreg[k];
+            if constexpr (VAL) a.s = gop<OP>(a.s, vreg[k]);
+            else if constexpr (RED) a.s += 1;
         }
     }
     // inclusive scan over the workgroup's threads, then the tile's exclusive prefix
@@ -138,7 +162,7 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const Seg y = seg_shfl_up(x, d);
-        if (lane >= (uint32_t)d) x = seg_combine(y, x);
+        if (lane >= (uint32_t)d) x = seg_combine<OP>(y, x);
     }
     if (lane == 63) {
         s_wc[w] = x.c;
@@ -146,16 +170,16 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
         s_wf[w] = x.f;
     }
     __syncthreads();
-    Seg wex{0, 0, 0}, tagg{0, 0, 0};
+    Seg wex{0, ID, 0}, tagg{0, ID, 0};
 #pragma unroll
     for (uint32_t v = 0; v < GT / 64; ++v) {
         const Seg sv{s_wc[v], s_ws[v], s_wf[v]};
-        if (v < w) wex = seg_combine(wex, sv);
-        tagg = seg_combine(tagg, sv);
+        if (v < w) wex = seg_combine<OP>(wex, sv);
+        tagg = seg_combine<OP>(tagg, sv);
     }
     Seg up = seg_shfl_up(x, 1);
-    if (lane == 0) up = Seg{0, 0, 0};
-    const Seg tex_thread = seg_combine(wex, up);
+    if (lane == 0) up = Seg{0, ID, 0};
+    const Seg tex_thread = seg_combine<OP>(wex, up);
     // decoupled look-back by wave 0, 64 predecessors per step: lane l reads tile t-1-l; the
     // window is combined oldest-first up to the nearest inclusive prefix (PRE), else whole
     if (w == 0) {
@@ -163,7 +187,7 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
             __hip_atomic_store(&st1[tile], gs_w1(kind, q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&st2[tile], gs_w2(kind, q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
-        Seg tex{0, 0, 0};
+        Seg tex{0, ID, 0};
         if (tile == 0) {
             if (lane == 0) publish(GS_PRE, tagg);
         } else {
@@ -188,19 +212,19 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
                     __builtin_amdgcn_s_sleep(1);
                     continue;
                 }
-                Seg x = j >= 0 && ((need >> lane) & 1ull) ? gs_value(w1, w2) : Seg{0, 0, 0};
+                Seg x = j >= 0 && ((need >> lane) & 1ull) ? gs_value(w1, w2) : Seg{0, ID, 0};
                 // oldest (highest lane) first: lane 0 ends with the window's combination
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) {
                     const Seg y{__shfl_down(x.c, d, 64), __shfl_down(x.s, d, 64), (uint32_t)__shfl_down((int)x.f, d, 64)};
-                    if (lane + d < 64) x = seg_combine(y, x);
+                    if (lane + d < 64) x = seg_combine<OP>(y, x);
                 }
                 x = Seg{__shfl(x.c, 0, 64), __shfl(x.s, 0, 64), (uint32_t)__shfl((int)x.f, 0, 64)};
-                tex = seg_combine(x, tex);
+                tex = seg_combine<OP>(x, tex);
                 if (pre) break;
                 top -= 64;
             }
-            if (lane == 0) publish(GS_PRE, seg_combine(tex, tagg));
+            if (lane == 0) publish(GS_PRE, seg_combine<OP>(tex, tagg));
         }
         if (lane == 0) {
             s_tc = tex.c;
@@ -209,7 +233,7 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
         }
     }
     __syncthreads();
-    const Seg ex = seg_combine(Seg{s_tc, s_ts, s_tf}, tex_thread);
+    const Seg ex = seg_combine<OP>(Seg{s_tc, s_ts, s_tf}, tex_thread);
     // emit: group g = ex.c + starts seen so far; a start closes group g - 1 with its sum.  The
     // tile's groups are [gt0, gt0 + tagg.c): staged in LDS (s_key / s_val are free: every
     // thread read its keys and values before the scan's barrier), then written coalesced
@@ -222,18 +246,19 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
         if (i < n) {
             if ((fm >> k) & 1u) {
                 const uint32_t q = (uint32_t)(g - gt0);
-                if constexpr (SUM) {
+                if constexpr (RED) {
                     if (q > 0) s_gsum[q - 1] = run;
                     else if (g > 0) vals[g - 1] = (int64_t)run;  // the group open at the tile's start
                 }
                 s_gkey[q] = kreg[k];
                 s_st[q] = (uint16_t)(tid * GI + k);
                 ++g;
-                run = 0;
+                run = ID;
             }
-            if constexpr (SUM) run += vreg[k];
+            if constexpr (VAL) run = gop<OP>(run, vreg[k]);
+            else if constexpr (RED) run += 1;
             if (i == n - 1) {
-                if constexpr (SUM) vals[g - 1] = (int64_t)run;
+                if constexpr (RED) vals[g - 1] = (int64_t)run;
                 *ngroups = (int64_t)g;
             }
         }
@@ -243,24 +268,30 @@ __global__ __launch_bounds__(GT) void k_group_fused(const ulonglong2 *__restrict
     for (uint32_t q = tid; q < ngt; q += GT) {
         gst(keys + gt0 + q, (int64_t)s_gkey[q]);
         if (starts) gst(starts + gt0 + q, t0 + (int64_t)s_st[q]);
-        if constexpr (SUM)
+        if constexpr (RED)
             if (q + 1 < ngt) gst(vals + gt0 + q, (int64_t)s_gsum[q]);  // (the tile's last group is still open)
     }
 }
 
 int64_t group_tiles(int64_t n) { return (n + GTILE - 1) / GTILE; }
 
-hipError_t launch_group_fused(const void *rec, int64_t n, bool sum, uint64_t *status, uint32_t *ticket, uint32_t *err,
+hipError_t launch_group_fused(const void *rec, int64_t n, int op, uint64_t *status, uint32_t *ticket, uint32_t *err,
                               int64_t *keys, int64_t *starts, int64_t *vals, int64_t *ngroups, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     const int64_t tiles = group_tiles(n);
     uint64_t *st2 = status + tiles;
-    if (sum)
-        hipLaunchKernelGGL(k_group_fused<true>, dim3((unsigned)tiles), dim3(GT), 0, st, (const ulonglong2 *)rec, n,
-                           status, st2, ticket, err, keys, starts, vals, ngroups);
-    else
-        hipLaunchKernelGGL(k_group_fused<false>, dim3((unsigned)tiles), dim3(GT), 0, st, (const ulonglong2 *)rec, n,
-                           status, st2, ticket, err, keys, starts, vals, ngroups);
+#define SGX_GROUP_LAUNCH(OP)                                                                                      \
+    hipLaunchKernelGGL(k_group_fused<OP>, dim3((unsigned)tiles), dim3(GT), 0, st, (const ulonglong2 *)rec, n, status, \
+                       st2, ticket, err, keys, starts, vals, ngroups)
+    switch (op) {
+    case GROUP_OP_NONE: SGX_GROUP_LAUNCH(GROUP_OP_NONE); break;
+    case GROUP_OP_SUM: SGX_GROUP_LAUNCH(GROUP_OP_SUM); break;
+    case GROUP_OP_MIN: SGX_GROUP_LAUNCH(GROUP_OP_MIN); break;
+    case GROUP_OP_MAX: SGX_GROUP_LAUNCH(GROUP_OP_MAX); break;
+    case GROUP_OP_COUNT: SGX_GROUP_LAUNCH(GROUP_OP_COUNT); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef SGX_GROUP_LAUNCH
     return hipGetLastError();
 }
 
@@ -317,8 +348,9 @@ hipError_t launch_digit_hist(const void *rec, int64_t n, int rb, uint32_t *hist,
 }
 
 // Map-side combine (reduceByKey's mapSideCombine = true): the combiners of one map task,
-// keys[g] and sums[g] of its groups, become 16 B (Long, Long) records again -- the map
-// output Spark writes after ExternalSorter.insertAll with an Aggregator.
+// keys[g] and vals[g] (the sum / min / max / count) of its groups, become 16 B (Long, Long)
+// records again -- the map output Spark writes after ExternalSorter.insertAll with an
+// Aggregator.
 __global__ __launch_bounds__(RT) void k_pack_pairs(const int64_t *__restrict__ keys, const int64_t *__restrict__ vals,
                                                    int64_t n, longlong2 *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;

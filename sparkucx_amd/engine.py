@@ -148,8 +148,11 @@ class ShuffleEngine:
         check(lib().sgx_set_compression(self.handle, shuffle_id, codes[codec], block_size), "setCompression")
 
     def set_map_side_combine(self, shuffle_id: int, agg: int = _lib.AGG_SUM):
-        """dep.mapSideCombine with a sum aggregator (reduceByKey): map outputs hold one
-        {key, sum} combiner per distinct key and partition."""
+        """dep.mapSideCombine with a reducing aggregator (AGG_SUM, AGG_MIN, AGG_MAX or
+        AGG_COUNT): map outputs hold one {key, combiner} record per distinct key and partition,
+        keys ascending within a partition -- the map's wrapping sum, signed minimum / maximum
+        of the key's values, or its record count.  ``read_grouped`` with the same ``agg``
+        merges the combiners (counts are summed)."""
         check(lib().sgx_set_map_side_combine(self.handle, shuffle_id, agg), "setMapSideCombine")
 
     def set_map_writer(self, shuffle_id: int, writer: str = "unsafe"):
@@ -459,8 +462,10 @@ class ShuffleEngine:
     def read_grouped(self, shuffle_id: int, map_ids: Sequence[int], start_partition: int, end_partition: int,
                      agg: int = _lib.AGG_GROUP, device: bool = False, out=None):
         """UcxShuffleReader.read with an aggregator on (Long, Long) records.  AGG_GROUP ->
-        (keys, group_starts, values); AGG_SUM -> (keys, sums).  Keys ascending per reducer,
-        values in canonical arrival order.  Host int64 arrays, or DeviceBuffers of int64 left
+        (keys, group_starts, values); every reducing aggregation -> (keys, values): AGG_SUM the
+        wrapping sums, AGG_MIN / AGG_MAX the signed minima / maxima, AGG_COUNT the groups'
+        record counts (on a map-side-combined shuffle: the merged combiners, counts summed).
+        Keys ascending per reducer, values in canonical arrival order.  Host int64 arrays, or DeviceBuffers of int64 left
         in HBM with ``device=True`` (the caller frees them).  ``out``: host int64 arrays
         (keys, group_starts or None, values) to fill instead of fresh ones -- as the JVM reader
         reuses its direct buffers -- at least as long as the result; the returned arrays are

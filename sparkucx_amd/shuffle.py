@@ -82,14 +82,21 @@ class RangePartitioner:
 
 @dataclass
 class Aggregator:
-    """Spark's Aggregator for the two combines the engine runs on (Long, Long) records:
+    """Spark's Aggregator for the combines the engine runs on (Long, Long) records:
     "group" = groupByKey (CompactBuffer append; Spark builds it with mapSideCombine = false),
-    "sum" = reduceByKey(_ + _) on Long values (wrapping), with or without map-side combine."""
+    "sum" = reduceByKey(_ + _) on Long values (wrapping),
+    "min" / "max" = reduceByKey(math.min) / reduceByKey(math.max) on signed Long values,
+    "count" = combineByKey(_ => 1L, (c, _) => c + 1, _ + _): records per key (combiners merge
+    by sum) -- the four reducing kinds with or without map-side combine."""
     kind: str = "group"
 
     def __post_init__(self):
-        if self.kind not in ("group", "sum"):
-            raise IllegalArgumentException(f"unsupported aggregator {self.kind!r} (group, sum)")
+        if self.kind not in _AGG_KINDS:
+            raise IllegalArgumentException(f"unsupported aggregator {self.kind!r} ({', '.join(_AGG_KINDS)})")
+
+
+_AGG_KINDS = {"group": _lib.AGG_GROUP, "sum": _lib.AGG_SUM, "min": _lib.AGG_MIN, "max": _lib.AGG_MAX,
+              "count": _lib.AGG_COUNT}
 
 
 _SERIALIZERS = {"fixed": _lib.SER_FIXED, "kryo": _lib.SER_KRYO,
@@ -117,9 +124,9 @@ class ShuffleDependency:
             # specified!")
             if self.aggregator is None:
                 raise IllegalArgumentException("Map-side combine without Aggregator specified!")
-            if self.aggregator.kind != "sum" or self.recordBytes != 16:
+            if self.aggregator.kind == "group" or self.recordBytes != 16:
                 raise UnsupportedOperationException(
-                    "map-side combine runs on the GPU for reduceByKey(_ + _) on (Long, Long) records")
+                    "map-side combine runs on the GPU for reduceByKey (sum, min, max, count) on (Long, Long) records")
         if self.serializer not in _SERIALIZERS:
             raise IllegalArgumentException(f"unknown serializer {self.serializer!r} (fixed, kryo)")
         if self.serializer == "kryo" and self.recordBytes != 16:
@@ -685,7 +692,8 @@ class UcxShuffleReader:
           key (ExternalSorter with an ordering, :166-181);
         * aggregator "group" (groupByKey, combineValuesByKey :155-164): (keys, group_starts,
           values) -- keys ascending per reducer, values in arrival order;
-        * aggregator "sum" (reduceByKey(_ + _)): (keys, sums).
+        * aggregator "sum" / "min" / "max" / "count" (reduceByKey, per-key counts): (keys,
+          one reduced value per key).
         Metrics as the reference's reader reports them: the range's blocks and bytes, and
         ``incRecordsRead`` with the shuffled records read (for an aggregator: the records it
         consumed, not its groups); a task killed before the read raises TaskKilledException
@@ -697,7 +705,7 @@ class UcxShuffleReader:
         if dep.aggregator is not None:
             if dep.recordBytes != 16:
                 raise UnsupportedOperationException("aggregation needs (Long, Long) 16 B records")
-            agg = _lib.AGG_SUM if dep.aggregator.kind == "sum" else _lib.AGG_GROUP
+            agg = _AGG_KINDS[dep.aggregator.kind]
             out = self.manager.engine.read_grouped(sid, self._maps(), self.start, self.end, agg)
             # the shuffled records the aggregator consumed, not its groups (the reference counts
             # ahead of combineValuesByKey / combineCombinersByKey, UcxShuffleReader.scala:148-162)
@@ -728,11 +736,11 @@ class UcxShuffleReader:
         if dep.aggregator is not None:
             if dep.recordBytes != 16:
                 raise UnsupportedOperationException("aggregation needs (Long, Long) 16 B records")
-            agg = _lib.AGG_SUM if dep.aggregator.kind == "sum" else _lib.AGG_GROUP
+            agg = _AGG_KINDS[dep.aggregator.kind]
             res = self.manager.engine.read_grouped(self.handle.shuffleId, self._maps(), self.start, self.end, agg)
             # the aggregator consumed every shuffled record before its first group comes out
             consumed = self.manager.engine.last_read_records()
-            if agg == _lib.AGG_SUM:
+            if agg != _lib.AGG_GROUP:
                 pairs = zip(res[0].tolist(), res[1].tolist())
             else:
                 keys, starts, vals = res
@@ -822,7 +830,7 @@ class UcxShuffleManager:
                                      getattr(p, "ascending", True), dependency.recordBytes,
                                      _SERIALIZERS[dependency.serializer])
         if dependency.mapSideCombine:
-            self.engine.set_map_side_combine(shuffleId, _lib.AGG_SUM)
+            self.engine.set_map_side_combine(shuffleId, _AGG_KINDS[dependency.aggregator.kind])
         h = self._handle_for(shuffleId, dependency)
         # spark.shuffle.compress (Spark 3.0.1's default: true) with spark.io.compression.codec
         # lz4 (the default): applied to Kryo shuffles, whose bytes are Spark's own; the fixed

@@ -2,7 +2,7 @@
 """Reduce-side timings on one GPU (UcxShuffleReader.read after the fetch): one map of N
 records (uniform or Zipf 16 B, or TeraSort 100 B with sampled RangePartitioner bounds) is
 written, then every reducer is read back sorted by key (sortByKey / TeraSort) or grouped
-(groupByKey, reduceByKey sum), on device memory.  Prints one JSON line per case with the
+(groupByKey, reduceByKey sum / min / max, per-key count), on device memory.  Prints one JSON line per case with the
 engine's per-stage HIP-event times (regroup = fetch gather, sort = LSD digit passes +
 partitioner pass, group = grouping kernels)."""
 import argparse
@@ -20,6 +20,9 @@ def main():
     ap.add_argument("--partitions", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--cases", default="sorted:uniform,group:uniform,sum:zipf,sorted:terasort")
+    ap.add_argument("--agg", action="append", choices=["group", "sum", "min", "max", "count"],
+                    help="an aggregated case <agg>:<--dist> (repeatable); given, it replaces --cases")
+    ap.add_argument("--dist", default="zipf", choices=["uniform", "zipf"], help="the key distribution of --agg cases")
     ap.add_argument("--flags", type=int, default=0, help="sgx_config.flags (64 = SGX_FLAG_NO_BUCKET_SORT)")
     a = ap.parse_args()
     import numpy as np
@@ -29,8 +32,12 @@ def main():
     e = sgx.ShuffleEngine(0, flags=a.flags)
     R = a.partitions
     sid = 0
-    for case in a.cases.split(","):
+    aggs = {"group": sgx.AGG_GROUP, "sum": sgx.AGG_SUM, "min": sgx.AGG_MIN, "max": sgx.AGG_MAX, "count": sgx.AGG_COUNT}
+    cases = [f"{g}:{a.dist}" for g in a.agg] if a.agg else a.cases.split(",")
+    for case in cases:
         op, dist = case.split(":")
+        if op != "sorted" and op not in aggs:
+            ap.error(f"unknown case {case!r}: sorted or one of {', '.join(aggs)}")
         sid += 1
         n = a.records if dist != "terasort" else a.records * 16 // 100
         rb = 100 if dist == "terasort" else 16
@@ -58,7 +65,7 @@ def main():
             e.read_sorted(sid, [0], 0, R, dst)
         e.stats_reset()
         walls, walls_host = [], []
-        agg = sgx.AGG_SUM if op == "sum" else sgx.AGG_GROUP
+        agg = aggs.get(op, sgx.AGG_GROUP)
         for _ in range(a.iters):
             t0 = time.perf_counter()
             if op == "sorted":
