@@ -470,6 +470,17 @@ int sgx_read_grouped(sgx_engine *e, int32_t shuffle_id, const int64_t *map_ids, 
  * of combineValuesByKey / combineCombinersByKey (spark_3_0/UcxShuffleReader.scala:148-162), so
  * an aggregated read reports these, not its groups. */
 int sgx_last_read_records(sgx_engine *e, int64_t *out_records);
+/* Which of its data-dependent branches the calling thread's last sort (inside sgx_read_sorted,
+ * sgx_read_grouped or a map-side combine) took; host state only, nothing runs on the GPU.  A
+ * read answered from the size query's result leaves the plan of that query.
+ *   out[0] path: 0 = LSD digit passes only; 1 = the bucket path (key-window passes, the pass by
+ *          the partitioner, every bucket sorted on chip) completed; 2 = the bucket sort met a
+ *          bucket longer than its halo and the digit passes finished
+ *   out[1] the key window's low bit (-1: no window was planned)   out[2] its width in bits
+ *   out[3] scatter passes launched before the bucket sort          out[4] digit passes run
+ *   out[5] 1 if passes ran inside the partitions' segments         out[6] 1 if the sort orders
+ *          by the shuffle's partitioner first                      out[7] 0 */
+int sgx_last_sort_plan(sgx_engine *e, int32_t out[8]);
 
 /* ---- RangePartitioner's bounds from the data (Spark 3.0.1 RangePartitioner: the
  *      rangeBounds initialiser, RangePartitioner.sketch and RangePartitioner.determineBounds;

@@ -147,6 +147,7 @@ SIGNATURES = {
     "sgx_read_grouped": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _i32,
                                         _vp, _vp]),
     "sgx_last_read_records": (ctypes.c_int, [_vp, _vp]),
+    "sgx_last_sort_plan": (ctypes.c_int, [_vp, _vp]),
     "sgx_progress": (ctypes.c_int, [_vp]),
     "sgx_sync": (ctypes.c_int, [_vp]),
     "sgx_stats_reset": (ctypes.c_int, [_vp]),

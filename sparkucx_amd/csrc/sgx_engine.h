@@ -307,6 +307,9 @@ struct Ctx {
     int host_slot = 0;
     // pre-aggregation records of the last read on this thread (sgx_last_read_records)
     int64_t last_read_records = 0;
+    // the plan of the last sort_records on this thread (sgx_last_sort_plan): path, window low
+    // bit, kbits, scatter passes before the bucket sort, digit passes, segmented, use_p, 0
+    int32_t last_sort_plan[8] = {0, -1, 0, 0, 0, 0, 0, 0};
     const uint32_t *last_off_dev = nullptr;  // device (R+1) record offsets of the last partition pass
     // The padded write's tail (its scan, the guarded two-pass fallback, the offsets' copy to the
     // host) runs on a second stream so that the next write's kernels do not queue behind it;

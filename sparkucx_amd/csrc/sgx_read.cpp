@@ -306,6 +306,10 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
         return fail_msg(SGX_ERR_UNSUPPORTED, "sorted read needs 16 B (Long, Long) or 100 B TeraSort records, not %d B",
                         rb);
     *sorted = c.sort_buf[0].p;
+    // what this call decides, for sgx_last_sort_plan (host variables only)
+    int32_t *plan = c.last_sort_plan;
+    for (int i = 0; i < 8; ++i) plan[i] = 0;
+    plan[1] = -1;
     if (n == 0) return SGX_OK;
     hipStream_t st = c.st;
     constexpr int MAXP = 12;
@@ -326,6 +330,7 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
     // holding > 1/16 of the records) keep the digit passes, whose trivial digits are skipped.
     // (a read of one partition needs no pass by the partitioner: every record has the same one)
     const bool use_p = by_partition && !range_asc && s.R > 1 && nparts != 1;
+    plan[6] = use_p ? 1 : 0;
     // Segmented passes: the gather of a fixed-codec read left partition p's records
     // contiguous (c.gather_part_recs), so every LSD pass can run inside each partition's segment
     // -- pieces of <= SEG_PIECE records, K4's SEG mode from per-piece offsets -- and the final
@@ -453,6 +458,8 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
                               (double)n / (rp * (double)(1ull << kbits)) <= max_avg;
         if (eligible) {
             const int lo = top - kbits;
+            plan[1] = lo;
+            plan[2] = kbits;
             // Segmented form: the gather left every partition's records
             // contiguous, so one stable pass by the window bits inside each partition's segment
             // replaces the window pass + the pass by the partitioner.
@@ -468,6 +475,7 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
                 cur ^= 1;
                 ++np;
                 seg_done = true;
+                plan[5] = 1;
             }
             for (int b0 = lo; b0 < top && !seg_done; b0 += 10) {  // least significant window chunk first
                 const int cb = std::min(10, top - b0);
@@ -491,6 +499,7 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
             // the last pass straight into the caller's device buffer when it has one (a sorted read
             // into HBM: no copy of the result afterwards)
             void *bout = final_dst ? final_dst : c.sort_buf[cur ^ 1].p;
+            plan[3] = np;
             HIP_TRY(launch_bucket_sort(c.sort_buf[cur].p, bout, n, rb, s.pp, use_p ? 1 : 0,
                                        (uint32_t)lo, (uint32_t)kbits, errs + np, st));
             SGX_TRY(debug_sync(e, st, "bucket sort"));
@@ -506,8 +515,10 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
                 HIP_TRY(hipEventRecord(t1, st));
                 e->record_stage(SGX_STAGE_SORT, t0, t1);
                 *sorted = bout;
+                plan[0] = 1;
                 return SGX_OK;
             }
+            plan[0] = 2;
             // a bucket too long for the chip: the digit passes below finish from the bucket
             // sort's input (stable passes: any stable order of the input sorts the same)
             HIP_TRY(hipMemsetAsync(c.sort_err.p, 0, MAXP * 4, st));
@@ -523,6 +534,8 @@ int sgx::sort_records(sgx_engine *e, Ctx &c, const Shuffle &s, int64_t n, bool b
             if (dh[(size_t)byte * 256 + (size_t)b] == (uint32_t)n) trivial = true;
         if (trivial && skip) continue;
         ++np;
+        ++plan[4];
+        if (seg_ok) plan[5] = 1;
         PartParams dp{};
         dp.kind = KIND_DIGIT;
         dp.R = DIGIT_R;
@@ -814,5 +827,16 @@ extern "C" int sgx_last_read_records(sgx_engine *e, int64_t *out) {
     Ctx *c = e->ctx();
     if (!c) return SGX_ERR_HIP;
     *out = c->last_read_records;
+    return SGX_OK;
+}
+
+// The plan of the calling thread's last sort_records (a sorted or grouped read, a map-side
+// combine): which of its data-dependent branches ran.  Host state only; for the tests.
+extern "C" int sgx_last_sort_plan(sgx_engine *e, int32_t out[8]) {
+    if (!e || !out) return fail_msg(SGX_ERR_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(e->device));
+    Ctx *c = e->ctx();
+    if (!c) return SGX_ERR_HIP;
+    for (int i = 0; i < 8; ++i) out[i] = c->last_sort_plan[i];
     return SGX_OK;
 }

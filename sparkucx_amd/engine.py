@@ -522,6 +522,16 @@ class ShuffleEngine:
         check(lib().sgx_last_read_records(self.handle, ctypes.byref(n)), "lastReadRecords")
         return int(n.value)
 
+    def last_sort_plan(self) -> dict:
+        """Which branches the calling thread's last sort took (sgx_last_sort_plan): path (0 digit
+        passes only, 1 bucket path, 2 bucket path gave up and the digit passes finished), the
+        key window's low bit ``lo`` (-1: none) and width ``kbits``, the scatter passes before
+        the bucket sort, the digit passes run, segmented, use_p.  For the tests."""
+        out = (ctypes.c_int32 * 8)()
+        check(lib().sgx_last_sort_plan(self.handle, out), "lastSortPlan")
+        names = ("path", "lo", "kbits", "window_passes", "digit_passes", "segmented", "use_p")
+        return dict(zip(names, (int(x) for x in out)))
+
     def range_bounds(self, batches: Sequence, nrecords: Sequence[int], record_bytes: int, num_partitions: int,
                      rdd_id: int = 0, sample_points_per_partition: int = 20,
                      parent_rdd_id: Optional[int] = None) -> np.ndarray:

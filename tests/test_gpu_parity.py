@@ -376,6 +376,37 @@ def test_range_directory_edges(engine, oracle_lib, shape, rb):
         check_against_oracle(engine, oracle_lib, recs, len(bounds) + 1, kind, bounds, asc)
 
 
+def test_range_bytes10_bounds_differ_in_low_bytes(engine, oracle_lib):
+    """PART_RANGE_BYTES10 decided by key bytes 8-9 alone: 24 groups of 8 bounds, a group sharing
+    its first 8 bytes and its bounds pairwise their first 8 or 9 (tails 0x0001 | 0x00FF | 0x0100
+    | 0x0101 | ...), and keys one below, on and one above every bound in the 16-bit tail -- the
+    +-1 carrying between bytes 9 and 8 -- plus random tails under the same prefixes and fully
+    random keys.  A compare that stopped after 8 bytes, or took bytes 8-9 in the wrong order,
+    moves records between partitions.  Against the oracle, both orders."""
+    import sparkucx_amd as sgx
+
+    rng = np.random.default_rng(8109)
+    n = 20_000
+    recs = oracle_lib.gen_terasort100(n, 78)
+    pre = np.unique(rng.integers(0, 256, (24, 8), dtype=np.uint8), axis=0)
+    tails = np.array([0x0001, 0x00FF, 0x0100, 0x0101, 0x7F00, 0x7FFF, 0x8000, 0xFFFE])
+
+    def keys_of(p, t):  # prefix rows p, 16-bit tails t -> 10-byte keys
+        t = np.asarray(t)
+        return np.concatenate([pre[p], np.stack([t >> 8, t & 0xFF], axis=1).astype(np.uint8)], axis=1)
+
+    gp = np.repeat(np.arange(len(pre)), len(tails))
+    bounds = np.ascontiguousarray(keys_of(gp, np.tile(tails, len(pre))))  # sorted: pre is, tails are
+    assert np.array_equal(bounds, bounds[np.lexsort(bounds.T[::-1])])
+    near = np.concatenate([keys_of(gp, np.tile(tails + d, len(pre))) for d in (-1, 0, 1)])
+    pick = rng.integers(0, len(near), 14_000)
+    recs[:14_000, :10] = near[pick]
+    recs[14_000:18_000, :10] = keys_of(rng.integers(0, len(pre), 4_000), rng.integers(0, 1 << 16, 4_000))
+    recs[:len(near), :10] = near  # every one of them at least once
+    for asc in (True, False):
+        check_against_oracle(engine, oracle_lib, recs, len(bounds) + 1, sgx.PART_RANGE_BYTES10, bounds, asc)
+
+
 @pytest.mark.parametrize("wide2", ["1", "0"])
 @pytest.mark.parametrize("R", [1, 7, 1000, 2048, 4096])
 @pytest.mark.parametrize("n", [1, 1023, 1024, 5 * 1024 + 77, 3 * 4096 + 1001])
